@@ -32,6 +32,23 @@ W warm-up steps.  The timed region is bracketed by barrier +
 torch.cuda.synchronize() on every rank and contains exactly K steps of the full
 request path; the reported time is the max over ranks.  Latency percentiles are
 client-side end-to-end (submit -> result received).
+
+A plain run does only that: set-up, W warm-up steps, K timed steps, the result
+line.  ``--dump-outputs DIR`` also keeps what the clients received for the last
+timed step (the last 32 x N requests issued) and writes it, after the timed
+region, as ``DIR/logits.npy`` (float32 [requests, classes], in issue order) and
+``DIR/payload_index.npy`` (float64: which of the 256 seeded payloads each row
+answers; the payloads are identical from run to run).  With N > 1 every driver
+rank writes its own share as ``logits.rank<r>.npy`` / ``payload_index.rank<r>.npy``.
+Row order is per load generator: with one generator (one rank, the default
+``--ingress-threads``) row i is the i-th of the last 32 requests issued; with
+several (more ranks, or ``--ingress-threads`` > 1) a file holds each
+generator's own last share, one generator after another, which is neither a
+global issue order nor one replica's last batch.  Compare two builds under the
+same arguments only, and pair rows through ``payload_index``.
+``--full`` is where anything beyond the headline figure belongs (other
+precisions, baselines, per-kernel figures); this script measures nothing of the
+kind today, so the option adds nothing yet.
 """
 from __future__ import annotations
 
@@ -83,6 +100,11 @@ def parse():
                     help="GEMM tile table to replay (auto = the MI355X table shipped for this config when it "
                          "exists; none = tune per shape and in context at start-up)")
     ap.add_argument("--json-out", default="")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the results the clients received for the last timed step to DIR/*.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement or check (none today); a plain run does only "
+                         "what the headline figure needs")
     ap.add_argument("--trace-out", default="", help="write a Chrome trace of the replicas' batches")
     ap.add_argument("--stamps-out", default="",
                     help="diagnostic: with the RDB_BLOCK_STAMPS kernel build (RDB_OPS_SO), save every block's start / "
@@ -129,6 +151,38 @@ def _fan_out(n: int) -> int:
     here = os.path.dirname(os.path.abspath(__file__))
     env["PYTHONPATH"] = here + (os.pathsep + env["PYTHONPATH"] if env.get("PYTHONPATH") else "")
     return subprocess.run(cmd, env=env).returncode
+
+
+def request_payloads(vocab_size: int, seq: int, rank: int = 0, count: int = 256):
+    """The `count` token-id sequences rank `rank`'s load generator cycles through
+    (seeded: the same requests in every run)."""
+    import torch
+
+    g = torch.Generator().manual_seed(1234 + rank)
+    out = []
+    for _ in range(count):
+        ids = torch.randint(1, vocab_size, (seq,), generator=g, dtype=torch.int32)
+        ids[0] = 101
+        out.append(ids)
+    return out
+
+
+def _dump_outputs(out_dir: str, gens, echo: bool, suffix: str) -> None:
+    """The last timed step's results as the clients received them, generator by
+    generator in issue order (a request that did not complete leaves a NaN row)."""
+    import numpy as np
+
+    kept = [k for lg in gens for k in lg.kept()]
+    # replica results are float32 logits; the echo rehearsal returns the head of the int32 payload
+    raw = np.dtype(np.int32 if echo else np.float32)
+    width = max([len(out) // raw.itemsize for _, st, out in kept if st == 0] + [1])
+    rows = np.full((len(kept), width), np.nan, dtype=np.float32)
+    for i, (_, st, out) in enumerate(kept):
+        if st == 0:
+            rows[i] = np.frombuffer(out, dtype=raw, count=width)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, f"logits{suffix}.npy"), rows)
+    np.save(os.path.join(out_dir, f"payload_index{suffix}.npy"), np.array([p for p, _, _ in kept], dtype=np.float64))
 
 
 def main():
@@ -226,12 +280,7 @@ def main():
     is_driver = rank in drivers
     G = args.ingress_threads or (1 if args.ingress == "per-rank" else min(4, max(1, n // 2)))
     if is_driver:
-        g = torch.Generator().manual_seed(1234 + rank)
-        payloads = []
-        for _ in range(256):
-            ids = torch.randint(1, cfg.vocab_size, (args.seq,), generator=g, dtype=torch.int32)
-            ids[0] = 101
-            payloads.append(ids.numpy().tobytes())
+        payloads = [ids.numpy().tobytes() for ids in request_payloads(cfg.vocab_size, args.seq, rank)]
         clients = [rjob.Client(job, seed=1234 + 64 * rank + i) for i in range(G)]
         gens = [rjob.LoadGen(c, 0, payloads) for c in clients]
         pool = ThreadPoolExecutor(G)
@@ -271,10 +320,11 @@ def main():
         conc = share(args.concurrency * n, n_drv, slot)
         rate = args.rate * n / n_drv
 
-        def drive(total, record, timeout_s):
+        def drive(total, record, timeout_s, keep=0):
             total = share(total, n_drv, slot)
+            keep = share(keep, n_drv, slot)
             futs = [pool.submit(gens[i].run, share(total, G, i), max(1, share(conc, G, i)), rate / G, 0.0,
-                                record, timeout_s) for i in range(G)]
+                                record, timeout_s, share(keep, G, i)) for i in range(G)]
             res = [f.result() for f in futs]
             if record:
                 for lg_i in gens[1:]:
@@ -297,7 +347,7 @@ def main():
     barrier()
     t0 = time.perf_counter()
     if is_driver:
-        result = drive(args.steps * per_step, True, 1200.0)
+        result = drive(args.steps * per_step, True, 1200.0, keep=per_step if args.dump_outputs else 0)
     barrier()
     sync()
     elapsed = time.perf_counter() - t0
@@ -309,6 +359,8 @@ def main():
         print(json.dumps({"rank": rank, "stamps": path, "dropped": stamps.dropped}), file=sys.stderr, flush=True)
         stamps.close()
     barrier()
+    if args.dump_outputs and is_driver:
+        _dump_outputs(args.dump_outputs, gens, echo, "" if world == 1 else f".rank{rank}")
     err = runner.error()
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64)

@@ -24,6 +24,7 @@
 #include <map>
 #include <random>
 #include <thread>
+#include <unordered_map>
 #include <vector>
 
 namespace py = pybind11;
@@ -466,9 +467,15 @@ class LoadGen {
   //  rate > 0        : open-loop Poisson arrivals at `rate` req/s (latency is
   //                    measured from the scheduled arrival, so client backlog counts)
   //  deadline_ms > 0 : per-request deadline (stale-drop path)
+  //  keep_last > 0   : keep the results of the last `keep_last` requests issued
+  //                    (read them with kept(); bench.py --dump-outputs)
   py::dict run(uint64_t total, int concurrency, double rate, double deadline_ms, bool record,
-               double timeout_s) {
+               double timeout_s, uint64_t keep_last) {
     if (record) hist_.reset();
+    keep_last = std::min(keep_last, total);
+    const uint64_t keep_from = total - keep_last;
+    keep_ids_.clear();
+    kept_.assign(keep_last, Kept{});
     uint64_t issued = 0, done = 0, ok = 0, dropped = 0, errors = 0, rejected = 0;
     int64_t in_flight = 0;
     std::vector<uint64_t> per_queue(c_.job().hdr()->n_queues, 0);
@@ -480,8 +487,17 @@ class LoadGen {
     std::deque<int64_t> backlog_t;
     size_t pi = 0;
     bool timed_out = false;
-    auto on_done = [&](SlotHeader* s, const char*) {
+    auto on_done = [&](SlotHeader* s, const char* out) {
       const int64_t t = now_ns();
+      if (!keep_ids_.empty()) {
+        auto it = keep_ids_.find(s->req_id);
+        if (it != keep_ids_.end()) {
+          Kept& k = kept_[it->second];
+          k.status = (int)s->status;
+          k.out.assign(out, s->len);
+          keep_ids_.erase(it);
+        }
+      }
       ++done;
       --in_flight;
       if (s->status == ST_OK) {
@@ -527,6 +543,10 @@ class LoadGen {
                                             dl > 0 ? t_sub + dl : 0);
           if (rid == -3) throw std::runtime_error("LoadGen payload larger than the request slot");
           if (rid < 0) { ++rejected; break; }
+          if (issued >= keep_from) {
+            keep_ids_[(uint64_t)rid] = (uint32_t)(issued - keep_from);
+            kept_[issued - keep_from].payload = (uint32_t)pi;
+          }
           pi = (pi + 1) % payloads_.size();
           ++issued;
           ++in_flight;
@@ -572,6 +592,14 @@ class LoadGen {
   }
   py::dict latency() const { return hist_dict(hist_); }
 
+  // Results kept by the last run(keep_last=n), in issue order: (index of the
+  // payload sent, completion status or -1 if it never completed, result bytes).
+  py::list kept() const {
+    py::list l;
+    for (const Kept& k : kept_) l.append(py::make_tuple(k.payload, k.status, py::bytes(k.out)));
+    return l;
+  }
+
   // The recorded latencies as plain numbers (bucket counts, count, sum, max) so
   // that generators living in OTHER processes can be folded in: bench.py at N
   // GPUs runs one ingress per rank and merges every rank's histogram on rank 0.
@@ -593,6 +621,13 @@ class LoadGen {
   uint32_t model_;
   std::vector<std::string> payloads_;
   Histogram hist_;
+  struct Kept {
+    uint32_t payload = 0;
+    int status = -1;
+    std::string out;
+  };
+  std::unordered_map<uint64_t, uint32_t> keep_ids_;
+  std::vector<Kept> kept_;
 };
 
 // ---------------------------------------------------------------------------
@@ -971,7 +1006,8 @@ PYBIND11_MODULE(_rdb_runtime, m) {
       .def(py::init<Client&, uint32_t, std::vector<std::string>>(), py::keep_alive<1, 2>())
       .def("run", &LoadGen::run, py::arg("total"), py::arg("concurrency") = 64,
            py::arg("rate") = 0.0, py::arg("deadline_ms") = 0.0, py::arg("record") = true,
-           py::arg("timeout_s") = 600.0)
+           py::arg("timeout_s") = 600.0, py::arg("keep_last") = 0)
+      .def("kept", &LoadGen::kept)
       .def("merge_from", &LoadGen::merge_from)
       .def("hist_state", &LoadGen::hist_state)
       .def("merge_state", &LoadGen::merge_state, py::arg("buckets"), py::arg("count"), py::arg("sum_ns"),

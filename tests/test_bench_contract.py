@@ -80,3 +80,50 @@ def test_bench_gpus_must_match_launcher_world_size():
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=120, cwd=ROOT,
                          env=dict(os.environ, WORLD_SIZE="2", RANK="0", LOCAL_RANK="0"))
     assert out.returncode == 2 and "WORLD_SIZE=2" in out.stderr
+
+
+def test_bench_dump_outputs_last_step_is_reproducible(tmp_path):
+    """--dump-outputs writes what the clients received for the last timed step
+    (the last 32 requests issued at one rank) as float32 rows in issue order, and
+    two runs with the same arguments write the same arrays."""
+    import numpy as np
+
+    steps, got = 6, []
+    for d in ("a", "b"):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1",
+               "--backend", "echo", "--echo-service-us", "200", "--dump-outputs", str(tmp_path / d)]
+        env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+        out = subprocess.run(cmd, capture_output=True, text=True, timeout=240, cwd=ROOT, env=env)
+        assert out.returncode == 0, out.stderr[-3000:]
+        line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
+        assert line["steps"] == steps and line["completed"] == steps * 32 and line["ms_per_step"] > 0
+        assert sorted(os.listdir(tmp_path / d)) == ["logits.npy", "payload_index.npy"]
+        got.append((np.load(tmp_path / d / "logits.npy"), np.load(tmp_path / d / "payload_index.npy")))
+    rows, idx = got[0]
+    assert rows.dtype == np.float32 and rows.shape == (32, 2) and idx.dtype == np.float64
+    # the echo replica answers with the first two tokens of the payload it was sent
+    assert (rows[:, 0] == 101).all() and (rows[:, 1] >= 1).all()
+    assert (idx == np.arange(steps * 32 - 32, steps * 32) % 256).all()
+    # ... so every row must be the answer to the payload payload_index names, not to a neighbour's
+    import importlib.util
+
+    from ray_dynamic_batching_amd.models.bert import BertConfig
+
+    spec = importlib.util.spec_from_file_location("rdb_bench_script", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    payloads = bench.request_payloads(BertConfig().vocab_size, 128)
+    second = np.array([int(payloads[int(i)][1]) for i in idx])
+    assert len(set(second.tolist())) > 16       # the named payloads differ in the echoed token
+    assert (rows[:, 1] == second).all()
+    assert (got[1][0] == rows).all() and (got[1][1] == idx).all()
+
+
+def test_bench_full_option_is_accepted():
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+           "--backend", "echo", "--echo-service-us", "200", "--full"]
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=240, cwd=ROOT, env=env)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1 and KEYS <= set(json.loads(lines[0]))

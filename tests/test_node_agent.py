@@ -2,8 +2,10 @@
 process supervision (restart with back-off, heartbeat loss, fail-pending +
 generation bump), and the Unix-socket control protocol."""
 import os
+import shutil
 import subprocess
 import sys
+import tempfile
 import time
 
 import pytest
@@ -168,7 +170,14 @@ def test_supervisor_heartbeat_loss_fails_pending_and_bumps_generation(tmp_path):
 
 
 def test_control_socket_protocol(tmp_path):
-    sock = str(tmp_path / "agent.sock")
+    # a Unix socket path holds at most 107 bytes (sockaddr_un.sun_path): pytest's
+    # tmp_path can be deeper than that, so the socket gets a short directory of its own:
+    # under the system's temporary directory, or under /tmp where even that is too deep
+    sock_dir = tempfile.mkdtemp(prefix="rdb_")
+    if len(os.path.join(sock_dir, "agent.sock").encode()) > 100:
+        shutil.rmtree(sock_dir, ignore_errors=True)
+        sock_dir = tempfile.mkdtemp(prefix="rdb_", dir="/tmp")
+    sock = os.path.join(sock_dir, "agent.sock")
     a = ragent.NodeAgent(2, 288.0, str(tmp_path / "kv.bin"))
     try:
         a.serve(sock)
@@ -183,3 +192,4 @@ def test_control_socket_protocol(tmp_path):
         assert st["gpus"][0]["used"] == 1.0 and st["procs"] == []
     finally:
         a.shutdown()
+        shutil.rmtree(sock_dir, ignore_errors=True)

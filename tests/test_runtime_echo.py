@@ -83,6 +83,34 @@ def test_loadgen_histogram_state_merges_like_merge_from():
         j.close()
 
 
+def test_loadgen_keeps_last_results_in_issue_order():
+    """run(keep_last=n) / kept(): the results of the last n requests ISSUED, in
+    issue order, each paired with the payload it answers -- although a slow and
+    a fast replica complete them out of order (bench.py --dump-outputs)."""
+    j = _job(2)
+    fast = rjob.EchoServer(j, 0, [0], max_batch=16, service_us=50.0, out_bytes=8)
+    slow = rjob.EchoServer(j, 1, [1], max_batch=16, service_us=3000.0, out_bytes=8)
+    fast.start()
+    slow.start()
+    try:
+        payloads = [bytes([i, 255 - i]) * 16 for i in range(37)]      # 37 does not divide the totals below
+        lg = rjob.LoadGen(rjob.Client(j, 0), 0, payloads)
+        res = lg.run(1000, 64, 0.0, 0.0, True, 60.0, keep_last=100)
+        assert res["ok"] == 1000 and min(res["per_queue"]) > 0        # both replicas answered
+        kept = lg.kept()
+        assert [k[0] for k in kept] == [i % 37 for i in range(900, 1000)]
+        assert all(st == 0 and out == payloads[p][:8] for p, st, out in kept)
+        # a later run starts afresh; keep_last is capped at the total; 0 keeps nothing
+        assert lg.run(10, 4, 0.0, 0.0, True, 60.0, keep_last=50)["ok"] == 10
+        kept = lg.kept()
+        assert [k[0] for k in kept] == list(range(10)) and all(out == payloads[p][:8] for p, _, out in kept)
+        assert lg.run(10, 4, 0.0, 0.0, True, 60.0)["ok"] == 10 and lg.kept() == []
+    finally:
+        fast.stop()
+        slow.stop()
+        j.close()
+
+
 def test_batches_form_under_load():
     j = _job(1)
     s = rjob.EchoServer(j, 0, [0], max_batch=32, service_us=500.0)
