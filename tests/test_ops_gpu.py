@@ -82,19 +82,28 @@ def test_linear_strided_rows():
     _close(ops.linear(cls, w, act="tanh"), ops.linear_ref(cls.contiguous(), w, act="tanh"), 2e-2, 2e-2)
 
 
-@pytest.mark.parametrize("D", [768, 1024, 4096, 320])
-def test_norms(D):
+def _norm_params(Ds):
+    """Every row length in both 16-bit dtypes; the bf16 cases keep their ids."""
+    return [pytest.param(D, dt, id=str(D) if dt == torch.bfloat16 else f"{D}-f16")
+            for dt in (torch.bfloat16, torch.float16) for D in Ds]
+
+
+@pytest.mark.parametrize("D,dtype", _norm_params([768, 1024, 4096, 320]))
+def test_norms(D, dtype):
     ops = _ops()
     torch.manual_seed(3)
-    x = torch.randn(300, D, device="cuda", dtype=torch.bfloat16)
-    r = torch.randn(300, D, device="cuda", dtype=torch.bfloat16)
-    g = torch.rand(D, device="cuda", dtype=torch.bfloat16) + 0.5
-    b = torch.randn(D, device="cuda", dtype=torch.bfloat16)
+    x = torch.randn(300, D, device="cuda", dtype=dtype)
+    r = torch.randn(300, D, device="cuda", dtype=dtype)
+    g = torch.rand(D, device="cuda", dtype=dtype) + 0.5
+    b = torch.randn(D, device="cuda", dtype=dtype)
     _close(ops.layer_norm(x, g, b), ops.layer_norm_ref(x, g, b), 3e-2, 2e-2)
     ro = torch.empty_like(x)
     _close(ops.layer_norm(x, g, b, residual=r, residual_out=ro), ops.layer_norm_ref(x, g, b, residual=r), 3e-2, 2e-2)
     _close(ro, x.float() + r.float(), 2e-2, 1e-2)
     _close(ops.rms_norm(x, g, 1e-5), ops.rms_norm_ref(x, g, 1e-5), 3e-2, 2e-2)
+    ro = torch.zeros_like(x)
+    _close(ops.rms_norm(x, g, 1e-5, residual=r, residual_out=ro), ops.rms_norm_ref(x, g, 1e-5, residual=r), 3e-2, 2e-2)
+    _close(ro, x.float() + r.float(), 2e-2, 1e-2)
 
 
 def test_embed_ln():
@@ -755,20 +764,24 @@ def test_se_scale_and_sigmoid_gemm():
     assert torch.allclose(y.float(), r.float(), atol=5e-3)
 
 
-@pytest.mark.parametrize("D", [100, 1664, 4100])
-def test_norms_non_multiple_of_256(D):
+@pytest.mark.parametrize("D,dtype", _norm_params([100, 1664, 4100]))
+def test_norms_non_multiple_of_256(D, dtype):
     from ray_dynamic_batching_amd import ops
 
     torch.manual_seed(D)
-    x = torch.randn(37, D, device="cuda", dtype=torch.bfloat16)
-    r = torch.randn(37, D, device="cuda", dtype=torch.bfloat16)
-    g = torch.rand(D, device="cuda", dtype=torch.bfloat16) + 0.5
-    b = torch.randn(D, device="cuda", dtype=torch.bfloat16)
+    x = torch.randn(37, D, device="cuda", dtype=dtype)
+    r = torch.randn(37, D, device="cuda", dtype=dtype)
+    g = torch.rand(D, device="cuda", dtype=dtype) + 0.5
+    b = torch.randn(D, device="cuda", dtype=dtype)
     y = ops.layer_norm(x, g, b, 1e-5, residual=r)
     ref = ops.layer_norm_ref(x, g, b, 1e-5, residual=r)
     assert torch.allclose(y.float(), ref.float(), atol=3e-2, rtol=3e-2)
     y2 = ops.rms_norm(x, g, 1e-5)
     assert torch.allclose(y2.float(), ops.rms_norm_ref(x, g, 1e-5).float(), atol=3e-2, rtol=3e-2)
+    ro = torch.zeros_like(x)
+    y3 = ops.rms_norm(x, g, 1e-5, residual=r, residual_out=ro)
+    assert torch.allclose(y3.float(), ops.rms_norm_ref(x, g, 1e-5, residual=r).float(), atol=3e-2, rtol=3e-2)
+    assert torch.allclose(ro.float(), x.float() + r.float(), atol=2e-2, rtol=1e-2)
 
 
 @pytest.mark.parametrize("M,N,K", [(1, 1000, 2048), (8, 2304, 768), (32, 768, 3072), (32, 2, 768),
