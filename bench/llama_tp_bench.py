@@ -9,6 +9,7 @@ broadcasts the token ids over RCCL and returns next-token ids.
 
     python bench/llama_tp_bench.py                      # TP=1 on one GPU
     torchrun --nproc-per-node 8 --master-addr 127.0.0.1 bench/llama_tp_bench.py
+    python bench/llama_tp_bench.py --quant fp8          # W8A8 projections (ops.linear_fp8)
 Reports per-batch prefill latency (p50 over replays) and prompts/s for
 batches 1, 2, 4, 8 of --seq tokens.
 """
@@ -41,6 +42,8 @@ def main(argv=None):
     ap.add_argument("--pipeline-depth", type=int, default=2)
     ap.add_argument("--json-out", default="")
     ap.add_argument("--checkpoint", default="", help="Hugging Face Llama checkpoint dir (each rank loads its shard)")
+    ap.add_argument("--quant", default="none", choices=["none", "fp8"],
+                    help="fp8: W8A8 projections (e4m3 weights and activations, ops.linear_fp8)")
     ap.add_argument("--allreduce", default="xgmi", choices=["xgmi", "rccl"],
                     help="TP all-reduce: custom push-based xGMI kernel (fused RMSNorm) or RCCL")
     a = ap.parse_args(argv)
@@ -63,19 +66,20 @@ def main(argv=None):
         if a.allreduce == "xgmi":
             # 8 prompts x seq tokens x hidden bf16 per all-reduce
             col.enable_xgmi("tp", max_elems=8 * a.seq * 4096)
-    cfg = LlamaConfig.llama3_8b(seq_len=a.seq, layers=a.layers)
+    cfg = LlamaConfig.llama3_8b(seq_len=a.seq, layers=a.layers, quant=a.quant)
+    prec = "bf16" if a.quant == "none" else "fp8 W8A8"
     t0 = time.time()
     if a.checkpoint:
         from ray_dynamic_batching_amd.models.weights import llama_from_hf
 
         m = llama_from_hf(a.checkpoint, seq_len=a.seq, tp_rank=rank, tp_size=world,
-                          group_name="tp" if world > 1 else None, device=f"cuda:{local}")
+                          group_name="tp" if world > 1 else None, device=f"cuda:{local}", quant=a.quant)
         cfg = m.cfg
     else:
         m = LlamaTP(cfg, rank, world, "tp" if world > 1 else None, device=f"cuda:{local}", init="shard")
     init_s = time.time() - t0
     if a.serve:
-        return _serve(a, m, world, rank)
+        return _serve(a, m, world, rank, prec)
     results = []
     for b in [int(x) for x in a.batches.split(",")]:
         ids = m.example_input(b, seed=b)
@@ -120,7 +124,7 @@ def main(argv=None):
                             tokens_per_s=round(tokens / p50 * 1e3, 1), tflops_whole_node=round(flops / p50 / 1e9, 1),
                             next_token=int(out[0, 0].item())))
     if rank == 0:
-        rep = dict(metric="Llama-3-8B bf16 TP prefill latency", tp=world, allreduce=a.allreduce if world > 1 else "none", seq_len=a.seq, layers=a.layers,
+        rep = dict(metric=f"Llama-3-8B {prec} TP prefill latency", quant=a.quant, tp=world, allreduce=a.allreduce if world > 1 else "none", seq_len=a.seq, layers=a.layers,
                    graph=not a.no_graph, init_s=round(init_s, 1), results=results,
                    data="synthetic token ids, random-init weights")
         print(json.dumps(rep), flush=True)
@@ -132,7 +136,7 @@ def main(argv=None):
         dist.destroy_process_group()
 
 
-def _serve(a, m, world, rank):
+def _serve(a, m, world, rank, prec="bf16"):
     """Config 4 serving: prompts -> shm queue -> rank-0 batching (<= 8) -> RCCL
     broadcast -> graph replay on every TP rank -> next-token completions."""
     import threading
@@ -151,7 +155,7 @@ def _serve(a, m, world, rank):
         job.configure_queue(0, 0, 0, 1024, 0.0, True)
     buckets = [1, 2, 4, 8]
     if a.loop == "native":
-        return _serve_native(a, m, world, rank, name, job, buckets)
+        return _serve_native(a, m, world, rank, name, job, buckets, prec)
     rep = TPReplica(m, name if rank == 0 else None, 0, 0, buckets, "tp" if world > 1 else None,
                     ring=f"{name}_ring").capture()
     if world > 1:
@@ -178,7 +182,7 @@ def _serve(a, m, world, rank):
         rep.step(0.01)
     rep.stop_all()
     lat = res["latency"]
-    rep_out = dict(metric="Llama-3-8B bf16 TP prefill serving (<= 8 prompts / batch)", tp=world, allreduce=a.allreduce if world > 1 else "none", seq_len=a.seq,
+    rep_out = dict(metric=f"Llama-3-8B {prec} TP prefill serving (<= 8 prompts / batch)", quant=a.quant, tp=world, allreduce=a.allreduce if world > 1 else "none", seq_len=a.seq,
                    layers=a.layers, prompts_per_s=round(res["ok"] / res["elapsed_s"], 1),
                    p50_ms=round(lat["p50_ms"], 3), p99_ms=round(lat["p99_ms"], 3), ok=res["ok"],
                    mean_batch=round(job.replica_stats(0)["batch_items"] / max(1, job.replica_stats(0)["batches"]), 2),
@@ -193,7 +197,7 @@ def _serve(a, m, world, rank):
     job.close()
 
 
-def _serve_native(a, m, world, rank, name, job, buckets):
+def _serve_native(a, m, world, rank, name, job, buckets, prec="bf16"):
     """The native TP loop (runtime/tp_replica.py NativeTP): rank 0's engine forms
     batches (first-arrival timeout), gathers them zero-copy on its copy stream and
     publishes them on the group's broadcast ring; followers copy + replay the same
@@ -231,7 +235,8 @@ def _serve_native(a, m, world, rank, name, job, buckets):
     st = job.replica_stats(0)
     ntp.stop()                                # STOP record: the followers leave
     lat = res["latency"]
-    rep_out = dict(metric="Llama-3-8B bf16 TP prefill serving (<= 8 prompts / batch)", loop="native engine",
+    rep_out = dict(metric=f"Llama-3-8B {prec} TP prefill serving (<= 8 prompts / batch)", quant=a.quant,
+                   loop="native engine",
                    compute_streams=a.compute_streams if world == 1 else 1,
                    tp=world, allreduce=a.allreduce if world > 1 else "none", seq_len=a.seq, layers=a.layers,
                    prompts_per_s=round(res["ok"] / res["elapsed_s"], 1), p50_ms=round(lat["p50_ms"], 3),

@@ -65,6 +65,11 @@ class LlamaConfig:
     eps: float = 1e-5
     max_position: int = 8192
     seq_len: int = 512
+    quant: str = "none"       # "fp8": W8A8 projections (e4m3 weights + per-channel scales, ops.linear_fp8)
+
+    def __post_init__(self):
+        if self.quant not in ("none", "fp8"):
+            raise ValueError(f"LlamaConfig.quant must be 'none' or 'fp8', got {self.quant!r}")
 
     @staticmethod
     def llama3_8b(**kw) -> "LlamaConfig":
@@ -148,9 +153,48 @@ class LlamaTP:
             w_down = col_shard(("down", i), D, cfg.intermediate, f0, f1)
             self.layers.append(dict(attn_norm=dev(torch.ones(D)), w_qkv=w_qkv, w_o=w_o,
                                     mlp_norm=dev(torch.ones(D)), w_gu=w_gu, w_down=w_down))
+            if cfg.quant == "fp8":
+                self._quantize_layer(self.layers[-1])    # layer by layer: no second 16-bit copy of the model
         self.final_norm = dev(torch.ones(D))
         self.lm_head = shard("lm_head", cfg.vocab_size, D, [(r * self.Vl, (r + 1) * self.Vl)])
         self.cos, self.sin = ops.rope_tables(cfg.max_position, Dh, cfg.rope_theta, device=self.device)
+
+    _PROJ = ("w_qkv", "w_o", "w_gu", "w_down")
+
+    @staticmethod
+    def _quantize_layer(L: dict) -> None:
+        """The four projections of this rank's shard -> (e4m3 bytes, f32 scale per
+        output row); the 16-bit matrices are dropped.  Norm weights stay 16-bit."""
+        for k in LlamaTP._PROJ:
+            if not isinstance(L[k], tuple):
+                L[k] = ops.quantize_weight_fp8(L[k])
+
+    def quantize_fp8(self) -> "LlamaTP":
+        """Quantise an already built / loaded 16-bit model in place (weights.llama_from_hf)."""
+        import dataclasses
+
+        self.cfg = dataclasses.replace(self.cfg, quant="fp8")
+        for L in self.layers:
+            self._quantize_layer(L)
+        return self
+
+    def layer_weight_bytes(self) -> int:
+        """Resident bytes of the layers' projection weights (scales included)."""
+        n = 0
+        for L in self.layers:
+            for k in self._PROJ:
+                for t in (L[k] if isinstance(L[k], tuple) else (L[k],)):
+                    n += t.numel() * t.element_size()
+        return n
+
+    def _proj(self, x, w, norm=None, **kw):
+        """One projection of the HIP path: ``linear(rms_norm(x) if norm else x)``.
+        FP8 weights take the activation as (e4m3 rows, row scales): from the fused
+        RMSNorm + quantise where a norm feeds the GEMM, else from the row quantiser."""
+        if isinstance(w, tuple):
+            xq, xs = (ops.rms_norm_fp8(x, norm, self.cfg.eps) if norm is not None else ops.quantize_fp8_rows(x))
+            return ops.linear_fp8(xq, xs, w[0], w[1], out_dtype=x.dtype, **kw)
+        return ops.linear(ops.rms_norm(x, norm, self.cfg.eps) if norm is not None else x, w, **kw)
 
     # -- servable contract: one prompt of seq_len tokens -> next-token id
     @property
@@ -218,14 +262,12 @@ class LlamaTP:
         if xg is not None and B * S * c.hidden <= xg.max_elems:
             return self._layers_hip_xgmi(x, B, S, xg)
         for L in self.layers:
-            h = ops.rms_norm(x, L["attn_norm"], c.eps)
-            qkv = ops.linear(h, L["w_qkv"])
+            qkv = self._proj(x, L["w_qkv"], norm=L["attn_norm"])
             ops.rope_(qkv, self.cos, self.sin, B, S, self.Hl, self.Hkvl, Dh)
             a = ops.attention(qkv, B, S, self.Hl, self.Hkvl, Dh, causal=True)
-            x = self._allreduce(ops.linear(a, L["w_o"], residual=x if first else None))
-            h = ops.rms_norm(x, L["mlp_norm"], c.eps)
-            g = ops.linear(h, L["w_gu"], act="swiglu")
-            x = self._allreduce(ops.linear(g, L["w_down"], residual=x if first else None))
+            x = self._allreduce(self._proj(a, L["w_o"], residual=x if first else None))
+            g = self._proj(x, L["w_gu"], norm=L["mlp_norm"], act="swiglu")
+            x = self._allreduce(self._proj(g, L["w_down"], residual=x if first else None))
         return x
 
     def _layers_hip_xgmi(self, x, B, S, xg):
@@ -240,15 +282,15 @@ class LlamaTP:
         h = ops.rms_norm(x, self.layers[0]["attn_norm"], c.eps)
         n = len(self.layers)
         for i, L in enumerate(self.layers):
-            qkv = ops.linear(h, L["w_qkv"])
+            qkv = self._proj(h, L["w_qkv"])
             ops.rope_(qkv, self.cos, self.sin, B, S, self.Hl, self.Hkvl, Dh)
             a = ops.attention(qkv, B, S, self.Hl, self.Hkvl, Dh, causal=True)
-            o = ops.linear(a, L["w_o"], residual=x if first else None)
+            o = self._proj(a, L["w_o"], residual=x if first else None)
             if self.pre_collective is not None:
                 self.pre_collective()
             x, h = xg.all_reduce_rmsnorm(o, L["mlp_norm"], c.eps)
-            g = ops.linear(h, L["w_gu"], act="swiglu")
-            d = ops.linear(g, L["w_down"], residual=x if first else None)
+            g = self._proj(h, L["w_gu"], act="swiglu")
+            d = self._proj(g, L["w_down"], residual=x if first else None)
             if self.pre_collective is not None:
                 self.pre_collective()
             if i + 1 < n:
@@ -275,9 +317,18 @@ class LlamaTP:
             tf = t.float()
             return (tf * torch.rsqrt(tf.pow(2).mean(-1, keepdim=True) + c.eps) * w.float()).to(t.dtype)
 
+        def lin(h, w):
+            if not isinstance(w, tuple):
+                return F.linear(h, w)
+            # W8A8 fake quantisation: the activation quantised per row and dequantised,
+            # the weight as its e4m3 values times the per-channel scale
+            q, s = ops.quantize_fp8_rows_ref(h)
+            hq = (q.float() * s[:, None]).to(h.dtype)
+            return F.linear(hq, (w[0].float() * w[1].float()[:, None]).to(h.dtype))
+
         for L in self.layers:
             h = rms(x, L["attn_norm"])
-            qkv = F.linear(h, L["w_qkv"])
+            qkv = lin(h, L["w_qkv"])
             q = rope(qkv[:, : self.Hl * Dh], self.Hl).transpose(1, 2)
             k = rope(qkv[:, self.Hl * Dh:(self.Hl + self.Hkvl) * Dh], self.Hkvl).transpose(1, 2)
             v = qkv[:, (self.Hl + self.Hkvl) * Dh:].reshape(B, S, self.Hkvl, Dh).transpose(1, 2)
@@ -285,14 +336,14 @@ class LlamaTP:
                 k = k.repeat_interleave(self.Hl // self.Hkvl, 1)
                 v = v.repeat_interleave(self.Hl // self.Hkvl, 1)
             a = F.scaled_dot_product_attention(q, k, v, is_causal=True).transpose(1, 2).reshape(B * S, self.Hl * Dh)
-            o = F.linear(a, L["w_o"])
+            o = lin(a, L["w_o"])
             if self.rank == 0:
                 o = o + x
             x = self._allreduce(o)
             h = rms(x, L["mlp_norm"])
-            gu = F.linear(h, L["w_gu"]).float()
+            gu = lin(h, L["w_gu"]).float()
             m = (F.silu(gu[:, 0::2]) * gu[:, 1::2]).to(x.dtype)
-            d = F.linear(m, L["w_down"])
+            d = lin(m, L["w_down"])
             if self.rank == 0:
                 d = d + x
             x = self._allreduce(d)

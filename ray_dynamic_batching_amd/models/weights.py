@@ -261,6 +261,9 @@ def llama_rope_tables(cfg, rope_scaling: Optional[dict], device=None):
 def load_llama_hf(model, src: Source, config: Optional[dict] = None, strict: bool = True):
     """Copy this rank's shard of a Hugging Face Llama checkpoint into ``model``
     (a ``LlamaTP``; any ``tp_rank`` / ``tp_size``)."""
+    if model.cfg.quant != "none":
+        raise ValueError("load_llama_hf fills 16-bit weights: load first, then model.quantize_fp8() "
+                         "(llama_from_hf(..., quant='fp8') does both)")
     hf = read_config(src, config)
     sd = _strip(load_state_dict(src), ("model.",))
     k = _Keys(sd)
@@ -301,14 +304,17 @@ def load_llama_hf(model, src: Source, config: Optional[dict] = None, strict: boo
 
 def llama_from_hf(src: Source, config: Optional[dict] = None, *, seq_len: int = 512, tp_rank: int = 0,
                   tp_size: int = 1, group_name: Optional[str] = None, device="cuda", dtype=torch.bfloat16,
-                  backend: str = "hip", strict: bool = True):
-    from .llama import LlamaTP
+                  backend: str = "hip", strict: bool = True, quant: str = "none"):
+    """``quant="fp8"``: the loaded shard's projections are quantised to e4m3 (W8A8)."""
+    from .llama import LlamaConfig, LlamaTP
 
     hf = read_config(src, config)
     cfg = _llama_config(hf, seq_len)
+    LlamaConfig(quant=quant)              # validates the mode before anything is loaded
     m = LlamaTP(cfg, tp_rank=tp_rank, tp_size=tp_size, group_name=group_name, device=device, dtype=dtype,
                 backend=backend)
-    return load_llama_hf(m, src, config=hf, strict=strict)
+    load_llama_hf(m, src, config=hf, strict=strict)
+    return m.quantize_fp8() if quant == "fp8" else m
 
 
 # ---------------------------------------------------------------------------

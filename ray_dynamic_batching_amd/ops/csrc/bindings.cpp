@@ -36,6 +36,15 @@ void gemm_rowln(uintptr_t A, int lda, uintptr_t W, uintptr_t bias, uintptr_t R, 
                 uintptr_t beta, uintptr_t C, int ldc, int M, int N, int K, float eps, uintptr_t stream);
 void norm_fwd(int dtype, int mode, uintptr_t x, uintptr_t res, uintptr_t res_out, uintptr_t gamma,
               uintptr_t beta, uintptr_t y, int rows, int D, int ldx, float eps, uintptr_t stream);
+void quant_fp8_rows(int dtype, uintptr_t x, int ldx, uintptr_t q, uintptr_t scale, int rows, int K,
+                    uintptr_t stream);
+void rms_norm_fp8(int dtype, uintptr_t x, uintptr_t res, uintptr_t res_out, uintptr_t gamma, uintptr_t q,
+                  uintptr_t scale, int rows, int D, int ldx, float eps, uintptr_t stream);
+void gemm_fp8(int out_dtype, int aux_dtype, uintptr_t A, int lda, uintptr_t W, int ldw, uintptr_t sa, uintptr_t sw,
+              uintptr_t C, int ldc, uintptr_t bias, uintptr_t R, int ldr, int M, int N, int K, int act, int tile,
+              uintptr_t stream);
+int gemm_fp8_num_tiles();
+int gemm_fp8_pick_tile(int M, int N);
 void embed_ln_fwd(int dtype, uintptr_t ids, uintptr_t types, uintptr_t word, uintptr_t pos,
                   uintptr_t typ, uintptr_t gamma, uintptr_t beta, uintptr_t y, int tokens, int S,
                   int D, int vocab, float eps, uintptr_t zero_stats, int zn, int zstride, uintptr_t stream);
@@ -111,6 +120,11 @@ PYBIND11_MODULE(_rdb_ops, m) {
   m.def("gemm_sk_workspace_size", &rdb::gemm_sk_workspace_size);
   m.def("norm_fwd", &rdb::norm_fwd, py::call_guard<py::gil_scoped_release>());
   m.def("embed_ln_fwd", &rdb::embed_ln_fwd, py::call_guard<py::gil_scoped_release>());
+  m.def("quant_fp8_rows", &rdb::quant_fp8_rows, py::call_guard<py::gil_scoped_release>());
+  m.def("rms_norm_fp8", &rdb::rms_norm_fp8, py::call_guard<py::gil_scoped_release>());
+  m.def("gemm_fp8", &rdb::gemm_fp8, py::call_guard<py::gil_scoped_release>());
+  m.def("gemm_fp8_num_tiles", &rdb::gemm_fp8_num_tiles, "block tiles of the FP8 GEMM (tile_cfg 0 .. n - 1)");
+  m.def("gemm_fp8_pick_tile", &rdb::gemm_fp8_pick_tile, "the tile the static (M, N) rule selects");
   m.def("attn_fwd", &rdb::attn_fwd, py::call_guard<py::gil_scoped_release>());
   m.def("qkv_attn_fwd", &rdb::qkv_attn_fwd, py::arg("dtype"), py::arg("X"), py::arg("ldx"), py::arg("Wp"),
         py::arg("bp"), py::arg("B"), py::arg("S"), py::arg("H"), py::arg("hidden"), py::arg("lens"), py::arg("out"),
