@@ -5,8 +5,10 @@
 #include <hip/hip_runtime.h>
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
+#include <map>
 #include <stdexcept>
 #include <string>
+#include <vector>
 
 namespace py = pybind11;
 
@@ -28,6 +30,10 @@ void gemm_tn_ln(uintptr_t A, int lda, uintptr_t W, int ldw, uintptr_t C, int ldc
                 uintptr_t panel, uintptr_t err, int a_parts, int r_parts);
 int gemm_stg_cfg(int cfg);
 int gemm_tile_bn(int cfg);
+std::map<std::string, std::vector<int>> gemm_tile_tables();
+std::map<std::string, long> gemm_tile_consts();
+std::map<std::string, std::vector<int>> conv_pp_tile_tables();
+std::map<std::string, std::vector<int>> conv_halo_tile_tables();
 void gemm_sk_bf16(uintptr_t A, int lda, uintptr_t W, int ldw, uintptr_t C, int ldc, uintptr_t bias, uintptr_t R,
                   int ldr, int M, int N, int K, float alpha, int act, uintptr_t workspace, int grid, int tile,
                   uintptr_t stream);
@@ -108,6 +114,13 @@ PYBIND11_MODULE(_rdb_ops, m) {
         py::call_guard<py::gil_scoped_release>());
   m.def("gemm_stg_cfg", &rdb::gemm_stg_cfg, "tile the staged-LayerNorm modes run for a requested cfg");
   m.def("gemm_tile_bn", &rdb::gemm_tile_bn, "N extent of tile cfg (partial-statistics count = ceil(N / BN))");
+  m.def("tile_tables", [] {
+    py::dict d;
+    for (const auto& kv : rdb::gemm_tile_consts()) d[py::str(kv.first)] = kv.second;
+    for (auto tables : {rdb::gemm_tile_tables, rdb::conv_pp_tile_tables, rdb::conv_halo_tile_tables})
+      for (const auto& kv : tables()) d[py::str(kv.first)] = py::tuple(py::cast(kv.second));
+    return d;
+  }, "the C++ tile tables, counts and encoding flags that ops/tiles.py copies (host only)");
   m.def("gemm_rowln", &rdb::gemm_rowln, py::call_guard<py::gil_scoped_release>());
 #ifdef RDB_EXPERIMENTAL_KERNELS
   constexpr bool experimental = true;

@@ -7,7 +7,10 @@
 //   * dwconv_nhwc  - depthwise conv (memory-bound; 8 channels per lane, 16-B loads)
 //   * maxpool_nhwc / avgpool_nhwc (global average pool feeding the FC GEMM)
 #include "gemm_core.h"
+#include <map>
 #include <stdexcept>
+#include <string>
+#include <vector>
 
 namespace rdb {
 
@@ -130,6 +133,13 @@ size_t conv_splitk_bytes(int M, int N, int cfg, int splits) {
   if (cfg & kConvHaloFlag) return 0;
   if (cfg & kConvPPFlag) return conv_pp_splitk_bytes(M, N, cfg & 255, splits);
   return splitk_bytes(M, N, cfg & 255, splits);
+}
+
+// The ping-pong conv tile geometry the Python candidate lists copy (ops/tiles.py).
+std::map<std::string, std::vector<int>> conv_pp_tile_tables() {
+  return {{"conv_pp_bm", {kConvPPBM, kConvPPBM + kNumConvPP}},
+          {"conv_pp_bn", {kConvPPBN, kConvPPBN + kNumConvPP}},
+          {"conv_pp_bk", {kConvPPBK, kConvPPBK + kNumConvPP}}};
 }
 
 // Depthwise RxR conv, NHWC f16, weights [R][R][C] (channel-contiguous), bias [C].

@@ -26,7 +26,10 @@
 // v_mfma_f32_16x16x32_f16 with the weight fragment as the MFMA A operand (the
 // accumulator holds 4 consecutive output channels of one pixel per lane).
 #include "gemm_core.h"
+#include <map>
 #include <stdexcept>
+#include <string>
+#include <vector>
 
 namespace rdb {
 
@@ -721,6 +724,11 @@ int conv_halo_tiles_s(int v, int N, int H, int W, int C, int K, int S) {
   return ((N + G - 1) / G) * ((P + TH - 1) / TH) * ((K + kHaloBN[v] - 1) / kHaloBN[v]);
 }
 int conv_halo_tiles(int v, int N, int H, int W, int C, int K) { return conv_halo_tiles_s(v, N, H, W, C, K, 1); }
+
+// The halo tile geometry the Python candidate lists copy (ops/tiles.py).
+std::map<std::string, std::vector<int>> conv_halo_tile_tables() {
+  return {{"halo_bm", {kHaloBM, kHaloBM + kNumHalo}}, {"halo_bn", {kHaloBN, kHaloBN + kNumHalo}}};
+}
 
 // Splits that actually run for `splits` requested over C / 64 channel blocks (every split non-empty).
 static int halo_eff_splits(int C, int splits, int& cpb) {

@@ -1300,6 +1300,9 @@ inline int stg_tile_cfg(int cfg) {
 
 // Heuristic: minimise (rounds of blocks over 256 CUs) x (tile work / tile efficiency).
 constexpr int kNumTiles4 = 13;  // tiles 0..12 are 4-wave (every loader); 13.. are 8-wave (dense only)
+// Ping-pong tiles with a split-K instantiation (the BK 64 ones, gemm_pp.h SK): with the
+// 4-wave tiles, the tiles whose kernels carry the split-K hand-off.
+constexpr bool pp_splitk_tile(int cfg) { return cfg == 19 || cfg == 21; }
 inline int pick_tile_cfg(int M, int N, bool dense) {
   int best = 3;
   double best_t = 1e30;
@@ -1500,7 +1503,7 @@ inline size_t splitk_bytes(int M, int N, int cfg, int splits) {
 inline LnEpi splitk_epi(int M, int N, int K, int cfg, int splits, void* ws, size_t ws_bytes) {
   LnEpi e{};
   // the 4-wave tiles, and the BK 64 ping-pong tiles 19 / 21 (gemm_pp.h SK instantiations)
-  if (splits < 2 || ws == nullptr || cfg < 0 || (cfg >= kNumTiles4 && cfg != 19 && cfg != 21)) return e;
+  if (splits < 2 || ws == nullptr || cfg < 0 || (cfg >= kNumTiles4 && !pp_splitk_tile(cfg))) return e;
   const int nk = (K + 63) / 64;
   const int kper = (nk + splits - 1) / splits;
   const int eff = (nk + kper - 1) / kper;
@@ -1523,7 +1526,7 @@ void launch_mfma_gemm(const P& ap, const T* W, int ldw, OutT* C, int ldc, const 
   if (cfg >= 0) cfg &= 0xFF;
   if (cfg < 0 || cfg >= (dense ? kNumTiles : kNumTiles4)) cfg = pick_tile_cfg(M, N, dense);
   // split-K runs on the 4-wave tiles (0..12) and the ping-pong tiles 19 / 21: their kernels carry the hand-off
-  const LnEpi e = (ln.sk_kper > 0 && (cfg < kNumTiles4 || cfg == 19 || cfg == 21) && act != ACT_SWIGLU) ? ln : LnEpi{};
+  const LnEpi e = (ln.sk_kper > 0 && (cfg < kNumTiles4 || pp_splitk_tile(cfg)) && act != ACT_SWIGLU) ? ln : LnEpi{};
   cfg |= deep;
   if (bias && R)
     launch_mfma_gemm_t<T, OutT, LoaderT, true, true>(ap, W, ldw, C, ldc, bias, R, ldr, M, N, K, alpha, act, s, cfg, e);

@@ -17,7 +17,11 @@
 // FFN-down take (LNR |) STATS.  Reference behaviour being preserved: the
 // BertLayer LayerNorms of the served models.
 #include "gemm_core.h"
+#include <iterator>
+#include <map>
 #include <stdexcept>
+#include <string>
+#include <vector>
 #include <string>
 
 namespace rdb {
@@ -156,5 +160,23 @@ void gemm_tn_ln(uintptr_t A, int lda, uintptr_t W, int ldw, uintptr_t C, int ldc
 
 int gemm_stg_cfg(int cfg) { return stg_tile_cfg(cfg); }
 int gemm_tile_bn(int cfg) { return cfg >= 0 && cfg < kNumTiles ? kTileBN[cfg] : -1; }
+
+// The tile geometry the Python candidate lists copy (ops/tiles.py), for the test that holds them equal.
+std::map<std::string, std::vector<int>> gemm_tile_tables() {
+  std::map<std::string, std::vector<int>> t;
+  t["bm"].assign(kTileBM, kTileBM + kNumTiles);
+  t["bn"].assign(kTileBN, kTileBN + kNumTiles);
+  t["nw"].assign(kTileNW, kTileNW + kNumTiles);
+  t["stg_tiles"].assign(std::begin(kStgTiles), std::end(kStgTiles));
+  for (int c = 0; c < kNumTiles; ++c) {
+    t["blocks_per_cu"].push_back(tile_blocks_per_cu(c));
+    if (pp_splitk_tile(c)) t["pp_splitk_tiles"].push_back(c);
+  }
+  return t;
+}
+std::map<std::string, long> gemm_tile_consts() {
+  return {{"num_tiles", kNumTiles}, {"num_tiles4", kNumTiles4}, {"deep_flag", kDeepFlag},
+          {"splitk_header", (long)kSplitKHeader}};
+}
 
 }  // namespace rdb

@@ -32,6 +32,6 @@ def test_tune_in_context_keeps_only_real_gains():
 
 def test_record_tuning_keys_collects_unique_keys():
     with ops.record_tuning_keys() as keys:
-        ops._KEY_LOG.append(("a",))
-        assert ops._KEY_LOG is keys
-    assert keys == [("a",)] and ops._KEY_LOG is None
+        ops.tuning._KEY_LOG.append(("a",))
+        assert ops.tuning._KEY_LOG is keys
+    assert keys == [("a",)] and ops.tuning._KEY_LOG is None

@@ -1,7 +1,8 @@
-"""Tile-choice encodings the conv / GEMM tuners rank (ops/__init__.py; decoded
+"""Tile-choice encodings the conv / GEMM tuners rank (ops/tiles.py; decoded
 by gemm_core.h launch_mfma_gemm / conv.hip): tile | splits << 8 | DEEP, and
 CONV_LINEAR | cfg for 1x1 convolutions on the dense GEMM tiles.  CPU-only:
-the candidate lists, not the kernels."""
+the candidate lists, not the kernels (tests/test_tile_tables.py holds the
+Python tables equal to the C++ ones)."""
 from ray_dynamic_batching_amd import ops
 
 
